@@ -18,8 +18,11 @@ the reference's ray.init + num_workers, paint_ppo.py:153,171).  Envs are sharded
 (weak scaling, 4096 per GPU, no data-path collective) and every 100 steps the ranks
 all_gather their episode returns over RCCL on a side stream.
 
-Prints ONE JSON line on rank 0 (see README / the task contract), including
-"roofline" for step_kernel and "cpu_baseline" (the C oracle on the host cores).
+Prints ONE JSON line on rank 0 (see README / the task contract).  A plain run times
+exactly --steps steps once and reports only the headline figures; --full times the
+region five times (median), samples single launches, and adds "roofline" for
+step_kernel, the launch occupancy and "cpu_baseline" (the C oracle on the host cores).
+--dump-outputs DIR writes what the last timed step returned as DIR/<name>.npy.
 """
 import argparse
 import json
@@ -36,12 +39,13 @@ ENVS_PER_GPU = 4096
 FRAGMENT = 100                  # rollout fragment length (paint_ppo.py:190 sample_batch_size)
 TIMING_EVERY = 8                # runs of > SAMPLE_ABOVE steps also bracket every 8th launch with its own HIP event
 SAMPLE_ABOVE = 256              # pair (a pair costs ~3.5 us of stream time, so short runs are left unperturbed)
-REPEATS = 5                     # the timed region (K steps) is run this many times; value = the median
+REPEATS = 5                     # --full: the timed region (K steps) is run this many times; value = the median
 PREWARM_SECONDS = 0.4           # untimed stepping of a scratch batch first: the timed region then runs at
                                 # the clocks a long job holds, also at the driver's --warmup 5 --steps 20
 HBM_PEAK_GBS = 8000.0           # MI355X_MICROARCH.md: HBM3E 8 TB/s
 CLOCK_GHZ = 2.4                 # MI355X_MICROARCH.md: max shader clock
 N_SIMD = 256 * 4                # 256 CUs x 4 SIMDs
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: at most this much in all (else a fixed sample of env rows)
 
 
 def algorithmic_bytes(dt, n_envs, obs_dim):
@@ -209,6 +213,28 @@ def cone_second_bound(step_us):
             'source': os.path.relpath(path, REPO) + ' (rocprofv3 --pmc: SQ_ACTIVE_INST_VALU x 4 / SIMD cycles, TA_TA_BUSY_sum / CU cycles); not measured in this run'}
 
 
+def dump_outputs(directory, arrays, suffix=''):
+    """Write {name: host array} as directory/<name><suffix>.npy, float32 / float64 (other types as float64).  Above
+    DUMP_LIMIT_BYTES in all, the same fixed seeded sample of env rows (axis 0) of every array is written instead, and
+    the sampled row numbers as env_rows."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    out = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        out[name] = a if a.dtype in (np.float32, np.float64) else a.astype(np.float64)
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_LIMIT_BYTES:
+        n = next(iter(out.values())).shape[0]
+        keep = max(1, n * (DUMP_LIMIT_BYTES - 8 * n) // total)
+        rows = np.sort(np.random.RandomState(0).choice(n, keep, replace=False))
+        out = {name: a[rows] for name, a in out.items()}
+        out['env_rows'] = rows.astype(np.float64)
+    for name, a in out.items():
+        np.save(os.path.join(directory, name + suffix + '.npy'), np.ascontiguousarray(a))
+    return sorted(out)
+
+
 # ---------------------------------------------------------------------------- self-launch (N > 1)
 def _free_port():
     s = socket.socket()
@@ -284,9 +310,17 @@ def main():
                          "the fine sheet, 'test' the coarse sheet with the reference's stale kd-tree, 'door_rr_big' the door on a "
                          'larger texture (the large-part kernels: Part_Dict door_lf .. door_rr_big, rge:106-117)')
     ap.add_argument('--tex', type=int, default=0, help='texture edge of --part (0 = its default); sets the sample count')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: leave out the CPU baseline')
     ap.add_argument('--no-prewarm', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='everything beyond the headline: the timed region %d times (value = the median), single launches '
+                         'sampled with their own HIP events, roofline, launch occupancy, CPU baseline' % REPEATS)
+    ap.add_argument('--dump-outputs', metavar='DIR',
+                    help='after the timed steps, write what the last timed step returned (observations, rewards, done, '
+                         'info, terminal observations; actions, log-probabilities and values where a policy acts) as '
+                         'DIR/<name>.npy')
     args = ap.parse_args()
+    repeats = REPEATS if args.full else 1
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         # plain `python bench.py --gpus N`: become the launcher.  Nothing above imported torch or touched HIP.
@@ -340,7 +374,7 @@ def main():
     sub_streams = [torch.cuda.Stream(device=device) for _ in subs] if len(subs) > 1 else [None]
     gen = torch.Generator(device=device)
     gen.manual_seed(1234 + rank)
-    total = args.warmup + REPEATS * args.steps
+    total = args.warmup + repeats * args.steps
     actions = torch.randint(0, 4, (total, args.envs), generator=gen, device=device, dtype=torch.int32)
     if args.actions == 'sweep':
         pattern = torch.tensor(([1] * 12 + [0] * 2 + [3] * 12 + [0] * 2), dtype=torch.int32, device=device)
@@ -403,6 +437,7 @@ def main():
         # the torch module wants float32; the fused kernel reads the env's float64 observations itself
         return env.obs.to(torch.float32) if args.policy == 'mlp-torch' else None
 
+    last = {'n': 0, 'policy': None}             # the last step's fragment length / policy outputs, for --dump-outputs
     graph = None
     if policy is not None and args.graph:
         # policy forward + sampling + env step captured once; the launch-bound inner loop becomes a replay
@@ -415,8 +450,9 @@ def main():
         torch.cuda.current_stream(device).wait_stream(side)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            act, _, _ = policy.act(obs_for_policy())
+            act, logp, value = policy.act(obs_for_policy())
             env.step_raw(act)
+        last['policy'] = [(act, logp, value)]       # the captured buffers: every replay writes them again
 
     import torch.distributed as dist
     gatherer = pdist.ReturnsGatherer(device) if dist.is_initialized() else None      # (world 1: only under PAINTRL_FORCE_DIST)
@@ -434,6 +470,7 @@ def main():
             if fragment_runner is not None:
                 n = min(FRAGMENT - (k % FRAGMENT), k1 - k)
                 fragment_runner.run(n)              # n policy + env steps in one persistent launch
+                last['n'] = n
                 k += n
             else:
                 if graph is not None:
@@ -447,16 +484,41 @@ def main():
                 elif len(subs) > 1:
                     # each env group alternates policy and env step on its own stream: one group's policy launch
                     # (latency bound, a few us) runs under the other group's env step
+                    outs = []
                     for g, e in enumerate(subs):
                         with torch.cuda.stream(sub_streams[g]):
-                            act, _, _ = group_policies[g].act(e.obs)
-                            e.step_raw(act)
+                            outs.append(group_policies[g].act(e.obs))
+                            e.step_raw(outs[-1][0])
+                    last['policy'] = outs
                 else:
-                    act, _, _ = policy.act(obs_for_policy(), gen)
+                    act, logp, value = policy.act(obs_for_policy(), gen)
                     env.step_raw(act)
+                    last['policy'] = [(act, logp, value)]
                 k += 1
             if gatherer is not None and k % FRAGMENT == 0:
                 gather_fragment()
+
+    def last_step_outputs():
+        """What a caller of the timed path received from its last step, on the host: the env rows of every group in
+        order; terminal observations only where the step ended an episode (zero elsewhere)."""
+        cat = lambda ts: torch.cat(ts) if len(ts) > 1 else ts[0]      # noqa: E731
+        if fragment_runner is not None:
+            fr, t = fragment_runner, last['n'] - 1
+            out = {'obs': fr.obs[0], 'reward': fr.reward[t], 'done': fr.done[t], 'info': fr.info[t],
+                   'final_obs': fr.final_obs[t]}                  # (run() has copied the last observation to row 0)
+            if args.policy == 'fragment':
+                out.update(action=fr.action[t], logp=fr.logp[t], value=fr.value[t])
+        else:
+            out = {'obs': cat([e.obs for e in subs]), 'reward': cat([e.reward for e in subs]),
+                   'done': cat([e.done_u8 for e in subs]), 'info': cat([e.info for e in subs]),
+                   'final_obs': cat([e.final_obs for e in subs])}
+            if last['policy'] is not None:
+                out.update(action=cat([p[0] for p in last['policy']]), logp=cat([p[1] for p in last['policy']]),
+                           value=cat([p[2] for p in last['policy']]))
+        stream_sync()
+        host = {name: t.detach().cpu().numpy() for name, t in out.items()}
+        host['final_obs'] = np.where(host['done'].reshape(-1, 1) != 0, host['final_obs'], 0.0)
+        return host
 
     run(0, args.warmup)
     stream_sync()
@@ -464,14 +526,14 @@ def main():
     # launches are back to back, the host runs ahead), divided by the launches -- an upper bound on the kernel's
     # duration (it includes the ~1 us dispatch gaps) that cannot exceed ms_per_step and does not perturb the run;
     # long runs additionally sample single launches with their own event pairs
-    timing_every = TIMING_EVERY if args.steps > SAMPLE_ABOVE else 0
+    timing_every = TIMING_EVERY if (args.full and args.steps > SAMPLE_ABOVE) else 0
     for e in subs:
         e.timing(timing_every)
     region_ok = len(subs) == 1 and graph is None
-    # the timed region -- EXACTLY --steps steps between barrier + synchronize on both sides, MAX over ranks -- REPEATS
-    # times back to back; the reported value is the median region
+    # the timed region -- EXACTLY --steps steps between barrier + synchronize on both sides, MAX over ranks -- once, or
+    # with --full REPEATS times back to back; the reported value is the median region
     elapsed_all, region_ms_all = [], []
-    for rep in range(REPEATS):
+    for rep in range(repeats):
         k0 = args.warmup + rep * args.steps
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         pdist.barrier()
@@ -492,8 +554,8 @@ def main():
         ms_, n_ = e.timing_read()
         kernel_ms, launches = kernel_ms + ms_, launches + n_
         e.timing(0)
-    order = sorted(range(REPEATS), key=lambda r: elapsed_all[r])
-    med = order[REPEATS // 2]
+    order = sorted(range(repeats), key=lambda r: elapsed_all[r])
+    med = order[repeats // 2]
     elapsed = elapsed_all[med]
 
     episodes = sum(int(e.state()['episode'].sum()) for e in subs) - args.envs
@@ -502,8 +564,10 @@ def main():
     if dist.is_initialized() and dist.get_world_size() > 1:          # (the returns' own all_gather path: RCCL or gloo)
         rank_devices = [int(v) for v in pdist.gather_returns(torch.tensor([float(local_rank)], dtype=torch.float64, device=device)).tolist()]
     occupancy = None
-    if args.paint_method == 'fast' and args.policy in ('random', 'mlp', 'mlp-torch'):
+    if args.full and args.paint_method == 'fast' and args.policy in ('random', 'mlp', 'mlp-torch'):
         occupancy = env.step_occupancy()                 # of one prl_batch_step launch
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, last_step_outputs(), '_rank%d' % rank if world > 1 else '')
     if rank == 0:
         n_launch_envs = args.envs // len(subs)
         survey_env, survey_launch, per_env, static, per_launch = algorithmic_bytes(dt, n_launch_envs, env.obs_dim)
@@ -512,15 +576,16 @@ def main():
         avg_kernel_s = None
         if region_ok and args.policy == 'random':
             avg_kernel_s = region_ms_all[med] / 1e3 / args.steps       # one step = one step_kernel launch
-            assert avg_kernel_s * 1e3 <= ms_per_step * 1.001, \
-                'kernel %.1f us > step %.1f us' % (avg_kernel_s * 1e6, ms_per_step * 1e3)
+            if args.full:
+                assert avg_kernel_s * 1e3 <= ms_per_step * 1.001, \
+                    'kernel %.1f us > step %.1f us' % (avg_kernel_s * 1e6, ms_per_step * 1e3)
         elif sampled_us:
             avg_kernel_s = sampled_us / 1e6
         achieved = survey_launch / avg_kernel_s / 1e9 if avg_kernel_s else None
         traffic, traffic_at = None, None
         tpath = os.path.join(REPO, 'profiles', 'hbm_traffic.json')
         # the committed PMC measurement is for the default workload (section / grid) only
-        if os.path.isfile(tpath) and args.envs == ENVS_PER_GPU and not args.mixed and args.actions == 'random' \
+        if args.full and os.path.isfile(tpath) and args.envs == ENVS_PER_GPU and not args.mixed and args.actions == 'random' \
                 and len(subs) == 1 and args.policy == 'random' and args.paint_method == 'fast' and not other_part and args.color_mode == 'RGB':
             with open(tpath) as f:
                 tj = json.load(f)
@@ -541,7 +606,7 @@ def main():
             'metric': 'batched env steps/sec (door panel, N=4096)', 'value': value,
             'unit': 'batched steps/s (%d envs each)' % args.envs, 'n_gpus': world, 'steps': args.steps,
             'warmup': args.warmup, 'ms_per_step': ms_per_step, 'higher_is_better': True,
-            'repeats': {'n': REPEATS, 'value_is': 'median', 'values': [world * args.steps / t for t in elapsed_all],
+            'repeats': {'n': repeats, 'value_is': 'median', 'values': [world * args.steps / t for t in elapsed_all],
                         'min': world * args.steps / max(elapsed_all), 'max': world * args.steps / min(elapsed_all)},
             'scaling': 'weak', 'vs_baseline': None, 'dtype': 'f64', 'data': 'synthetic',
             'config': {'workload': 'PaintGymEnv %s%s, OBS_MODE=%r%s, %d envs per GPU, '
@@ -565,31 +630,32 @@ def main():
                                       % (world, dist_world, dist.get_backend() if dist.is_initialized() else 'none')
                                       + (', %d independent env groups per GPU on %d streams' % (len(subs), len(subs))
                                          if len(subs) > 1 else '')},
-            'roofline': {'bound': 'hbm', 'kernel': ('step_kernel' if env.mask_stride <= 256 else 'step_kernel_big') if args.paint_method == 'fast' else 'the five launches of a cone-beam step (path, beams, rest, far, finish)', 'achieved': achieved, 'peak': HBM_PEAK_GBS,
-                         'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS if achieved else None, 'traffic': traffic,
-                         'traffic_over_algorithmic': traffic / survey_launch if traffic else None,
-                         'traffic_measured_at': traffic_at,
-                         'traffic_from': 'profiles/hbm_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, '
-                                         'FETCH_SIZE x2 calibrated on copy_mask_kernel); not measured in this run.  About 11 MB '
-                                         'of that figure are part tables fetched again in every launch only because rocprofv3 --pmc '
-                                         'invalidates the L2s between dispatches (profiles/r04_l2_cold_under_pmc.txt): an artefact '
-                                         'of counter collection, absent from the unprofiled back-to-back launches this line times',
-                         'algorithmic_bytes_per_env_step': survey_env, 'bytes_per_launch': survey_launch,
-                         'layout_bytes_per_env_step': per_env, 'layout_static_table_bytes': static,
-                         'layout_bytes_per_launch': per_launch,
-                         'avg_kernel_us': avg_kernel_s * 1e6 if avg_kernel_s else None,
-                         'launches_timed': args.steps if (region_ok and args.policy == 'random') else int(launches),
-                         'kernel_time_from': 'one HIP event pair on the launch stream around the timed region / launches '
-                                             '(upper bound: includes dispatch gaps)' if (region_ok and args.policy == 'random')
-                                             else 'HIP event pairs around sampled launches',
-                         'avg_kernel_us_sampled': sampled_us, 'sampled_launches': int(launches),
-                         'second_bound': valu_issue_bound(avg_kernel_s * 1e6 if avg_kernel_s else None, args.obs_mode)
-                         if (args.envs == ENVS_PER_GPU and not args.mixed and args.policy == 'random' and args.actions == 'random'
-                             and args.paint_method == 'fast' and len(subs) == 1 and not other_part and args.color_mode == 'RGB') else
-                         (cone_second_bound(1e3 * ms_per_step) if (args.paint_method == 'normal' and args.envs == ENVS_PER_GPU
-                                                                    and not args.mixed and len(subs) == 1) else None)},
         }
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full:
+            out['roofline'] = {'bound': 'hbm', 'kernel': ('step_kernel' if env.mask_stride <= 256 else 'step_kernel_big') if args.paint_method == 'fast' else 'the five launches of a cone-beam step (path, beams, rest, far, finish)', 'achieved': achieved, 'peak': HBM_PEAK_GBS,
+                               'unit': 'GB/s', 'frac': achieved / HBM_PEAK_GBS if achieved else None, 'traffic': traffic,
+                               'traffic_over_algorithmic': traffic / survey_launch if traffic else None,
+                               'traffic_measured_at': traffic_at,
+                               'traffic_from': 'profiles/hbm_traffic.json (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE in separate passes, '
+                                               'FETCH_SIZE x2 calibrated on copy_mask_kernel); not measured in this run.  About 11 MB '
+                                               'of that figure are part tables fetched again in every launch only because rocprofv3 --pmc '
+                                               'invalidates the L2s between dispatches (profiles/r04_l2_cold_under_pmc.txt): an artefact '
+                                               'of counter collection, absent from the unprofiled back-to-back launches this line times',
+                               'algorithmic_bytes_per_env_step': survey_env, 'bytes_per_launch': survey_launch,
+                               'layout_bytes_per_env_step': per_env, 'layout_static_table_bytes': static,
+                               'layout_bytes_per_launch': per_launch,
+                               'avg_kernel_us': avg_kernel_s * 1e6 if avg_kernel_s else None,
+                               'launches_timed': args.steps if (region_ok and args.policy == 'random') else int(launches),
+                               'kernel_time_from': 'one HIP event pair on the launch stream around the timed region / launches '
+                                                   '(upper bound: includes dispatch gaps)' if (region_ok and args.policy == 'random')
+                                                   else 'HIP event pairs around sampled launches',
+                               'avg_kernel_us_sampled': sampled_us, 'sampled_launches': int(launches),
+                               'second_bound': valu_issue_bound(avg_kernel_s * 1e6 if avg_kernel_s else None, args.obs_mode)
+                               if (args.envs == ENVS_PER_GPU and not args.mixed and args.policy == 'random' and args.actions == 'random'
+                                   and args.paint_method == 'fast' and len(subs) == 1 and not other_part and args.color_mode == 'RGB') else
+                               (cone_second_bound(1e3 * ms_per_step) if (args.paint_method == 'normal' and args.envs == ENVS_PER_GPU
+                                                                          and not args.mixed and len(subs) == 1) else None)}
+        if world == 1 and args.full and not args.no_cpu_baseline:
             # (a bounded sample: the oracle's step scales with the part's sample count)
             out['cpu_baseline'] = cpu_baseline(tables, steps_sample=max(24, int(300 * 9664 / max(9664, dt.n_samples))),
                                                n_envs=args.envs, obs_mode=args.obs_mode, overlap=overlap)

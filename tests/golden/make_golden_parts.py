@@ -6,8 +6,8 @@
 2. episodes_door_big.npz + g0_tables_door_big.npz: the synthetic door on a 480 x 480 texture ('door_rr_big',
    ~38 000 front samples: the large-part kernels), recorded from the reference like every other fixture.
 3. episodes_reference_door_rr.npz: one episode on the reference's own door_rr.urdf (Part_NO 5), for the
-   in-container check of the CPU oracle against the reference on a real large part (tables are rebuilt from
-   /root/reference at test time; the test is skipped where the reference is absent).
+   check of the CPU oracle against the reference on a real large part (tables are rebuilt at test time from the
+   reference's part files stored under tests/golden/reference_parts/).
 
     python tests/golden/make_golden_parts.py [digests] [big] [door_rr] [reference_meshes] [hsi] [hsi_cone] [sparse]
 """
@@ -101,9 +101,8 @@ def reference_meshes(which=('door_test', 'square')):
     """Episodes on the two parts the reference's published results use, on the reference's OWN meshes (rge:106-108:
     door_test.urdf = Part_NO 0, square.urdf = Part_NO 1; zigzag.py:8, spiral.py:8, paint_ppo.py:95): section observation
     from 'all' and anchor starts, grid + both penalties, the cone beams, COLOR_MODE 'HSI', and the texture image at the
-    end of one episode (the real pattern.jpg under the labels).  Replayed by the oracle on tables rebuilt from
-    /root/reference at test time (tests/test_reference_parts.py, skipped where the reference is absent): the meshes do
-    not travel, the recorded trajectories do."""
+    end of one episode (the real pattern.jpg under the labels).  Replayed by the oracle on tables rebuilt at test time
+    from the reference's part files stored under tests/golden/reference_parts/ (tests/test_reference_parts.py)."""
     from make_golden import texture_of, zigzag_policy
     root = os.path.join(ref_import.REFERENCE_ROOT, 'PaintRLEnv')
     for part_no, name in ((0, 'door_test'), (1, 'square')):

@@ -106,6 +106,34 @@ def test_bench_launcher_names_the_failing_rank():
     assert 'of 8 exited with status' in out.stderr, out.stderr[-1500:]
 
 
+
+def test_bench_dump_outputs_keeps_a_fixed_sample_within_its_limit(tmp_path, monkeypatch):
+    """`bench.py --dump-outputs` writes float32 / float64 files: all rows when they fit, else the same seeded sample of
+    env rows from every array (and the sampled row numbers) within DUMP_LIMIT_BYTES, identical from call to call."""
+    sys.path.insert(0, REPO)
+    import bench
+    n = 1000
+    arrays = {'obs': np.arange(n * 6, dtype=np.float64).reshape(n, 6), 'done': (np.arange(n) % 3 == 0).astype(np.uint8),
+              'action': np.arange(n, dtype=np.int32)}
+    assert bench.dump_outputs(str(tmp_path / 'all'), arrays) == ['action', 'done', 'obs']
+    for name, a in arrays.items():
+        got = np.load(str(tmp_path / 'all' / (name + '.npy')))
+        assert got.dtype in (np.float32, np.float64) and np.array_equal(got, a)
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 20000)
+    for tag in ('a', 'b'):
+        assert bench.dump_outputs(str(tmp_path / tag), arrays, '_rank1') == ['action', 'done', 'env_rows', 'obs']
+    files = sorted(os.listdir(str(tmp_path / 'a')))
+    assert files == ['action_rank1.npy', 'done_rank1.npy', 'env_rows_rank1.npy', 'obs_rank1.npy']
+    got = {f: np.load(str(tmp_path / 'a' / f)) for f in files}
+    assert sum(a.nbytes for a in got.values()) <= 20000 and all(a.dtype in (np.float32, np.float64) for a in got.values())
+    for f in files:
+        assert np.array_equal(got[f], np.load(str(tmp_path / 'b' / f)))
+    rows = got['env_rows_rank1.npy'].astype(np.int64)
+    assert 0 < rows.size < n and np.all(np.diff(rows) > 0)
+    assert np.array_equal(got['obs_rank1.npy'], arrays['obs'][rows]) and np.array_equal(got['action_rank1.npy'], rows)
+    assert np.array_equal(got['done_rank1.npy'], arrays['done'][rows])
+
+
 def _forced_single_rank(rank, world, port, out_dir):
     sys.path.insert(0, REPO)
     os.environ.update(RANK='0', LOCAL_RANK='0', WORLD_SIZE='1', MASTER_ADDR='127.0.0.1', MASTER_PORT=str(port),

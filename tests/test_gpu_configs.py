@@ -172,7 +172,7 @@ def test_bench_self_launches_its_ranks(tmp_path, ranks):
     env.pop('WORLD_SIZE', None)
     env.pop('RANK', None)
     out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', str(ranks), '--steps', '120', '--warmup',
-                          '10', '--envs', '512', '--no-cpu-baseline'], env=env, capture_output=True, text=True,
+                          '10', '--envs', '512', '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True,
                          timeout=900)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
@@ -180,6 +180,34 @@ def test_bench_self_launches_its_ranks(tmp_path, ranks):
     rec = json.loads(lines[0])
     assert rec['n_gpus'] == ranks and 'world size %d' % ranks in rec['config']['parallelism']
     assert rec['value'] > 0 and rec['roofline']['avg_kernel_us'] <= 1e3 * rec['ms_per_step'] * 1.001
+
+
+
+def test_plain_bench_times_its_steps_once_and_dumps_the_same_outputs_twice(tmp_path):
+    """A plain `bench.py` run times exactly --steps steps in one region and prints the headline only (no roofline, no
+    CPU baseline); --dump-outputs writes the last timed step's arrays (float32 / float64), equal from run to run."""
+    env = dict(os.environ)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'PAINTRL_FORCE_DIST'):
+        env.pop(k, None)
+    recs = []
+    for tag in ('a', 'b'):
+        out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '40', '--warmup', '5',
+                              '--envs', '1024', '--dump-outputs', str(tmp_path / tag)], env=env, capture_output=True,
+                             text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-3000:]
+        lines = [l for l in out.stdout.splitlines() if l.startswith('{')]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+    for rec in recs:
+        assert all(k in rec for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'))
+        assert rec['steps'] == 40 and rec['repeats']['n'] == 1 and 'roofline' not in rec and 'cpu_baseline' not in rec
+        assert abs(rec['value'] * rec['ms_per_step'] - 1e3) < 1e-6 * 1e3
+    names = sorted(os.listdir(str(tmp_path / 'a')))
+    assert names == sorted(os.listdir(str(tmp_path / 'b')))
+    assert {'obs.npy', 'reward.npy', 'done.npy', 'info.npy', 'final_obs.npy'} <= set(names)
+    for f in names:
+        a, b = np.load(str(tmp_path / 'a' / f)), np.load(str(tmp_path / 'b' / f))
+        assert a.dtype in (np.float32, np.float64) and a.shape[0] == 1024 and np.array_equal(a, b), f
 
 
 _RCCL_SCRIPT = r'''
@@ -240,7 +268,7 @@ def test_bench_reports_the_rccl_backend_under_force_dist():
     for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK', 'PAINTRL_DIST_BACKEND'):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(REPO, 'bench.py'), '--gpus', '1', '--steps', '60', '--warmup', '10',
-                          '--envs', '1024', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
+                          '--envs', '1024', '--full', '--no-cpu-baseline'], env=env, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     rec = json.loads([l for l in out.stdout.splitlines() if l.startswith('{')][0])
     assert rec['n_gpus'] == 1 and 'backend nccl' in rec['config']['parallelism']

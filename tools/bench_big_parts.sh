@@ -9,7 +9,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/${TAG}_big$SUF
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py"
+B="python3 $ROOT/bench.py --full"
 for spec in door_rr:328 door_rf:448 door_rr_big:652; do
   name=${spec%%:*}; tex=${spec##*:}
   echo "== $name (texture $tex)"

@@ -8,7 +8,7 @@ ROOT=$(cd "$(dirname "$0")/.." && pwd)
 OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py"
+B="python3 $ROOT/bench.py --full"
 W="python3 $ROOT/tools/run_workload.py"
 
 echo "== bench lines"
