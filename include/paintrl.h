@@ -204,6 +204,30 @@ int prl_batch_get_thickness(PrlBatch *batch, uint8_t *thick, void *stream);
  * {i32 last_episode_len, last_episode_painted}.  facet_hint is a cache (the collision triangle the
  * previous ray hit, -1 = none), not reference state: any value gives the same results. */
 int prl_batch_get_state(PrlBatch *batch, double *state, void *stream);
+/* Snapshots of env state (no reference counterpart: the reference's envs cannot be saved; ALE cloneState, MuJoCo set_state).
+ * What carries an env from one step to the next is its state record, coverage row, last-shot row and, for COLOR_MODE 'HSI',
+ * thickness row; a snapshot row holds exactly these, dense, in device sample order:
+ *   state f64[n][PRL_STATE_DOUBLES], painted u64[n][mask_stride], last u64[n][mask_stride],
+ *   thick u8[n][64 * mask_stride] (must be non-NULL exactly when the batch is HSI), part i32[n] (the env's part id).
+ * All index and data pointers are device pointers, 8-byte aligned (16-byte aligned buffers are moved 16 bytes a lane).  Both
+ * calls are stream-ordered and do not synchronise; an export followed by an import on the same stream reads every source row
+ * before it writes any destination, so swapping or rotating envs of one batch needs no special care.
+ *
+ * Export: snapshot row k <- env env_idx[k] for k < n (env_idx NULL = identity).  An env index out of range gives part[k] = -1
+ * and leaves the rest of row k unwritten. */
+int prl_batch_export(PrlBatch *batch, int n, const int32_t *env_idx, double *state, uint64_t *painted, uint64_t *last,
+                     uint8_t *thick, int32_t *part, void *stream);
+/* Import: env env_idx[k] <- snapshot row row_idx[k] for k < n, from a snapshot of n_rows rows (env_idx / row_idx NULL =
+ * identity).  One row may go to many envs (cloning); the env indices of one call must be distinct.  painted and last are
+ * ANDed with the part's valid bits, the library's index of the last-shot row is rebuilt exactly, HSI bytes of pad samples
+ * are set to 255 and a facet hint outside the part's collision set becomes -1.  A pair whose env or row index is out of
+ * range, or whose part[row] is not the env's part, is skipped (that env is left as it was) and counted in *n_skipped
+ * (device i32, added to, or NULL).  The episode counter is taken over: a clone draws its later auto-reset start points
+ * with the episode of its source and its OWN env index. */
+int prl_batch_import(PrlBatch *batch, int n, int n_rows, const int32_t *env_idx, const int32_t *row_idx, const double *state,
+                     const uint64_t *painted, const uint64_t *last, const uint8_t *thick, const int32_t *part,
+                     int32_t *n_skipped, void *stream);
+
 /* Episode returns (rge:359-360 _total_return of the last finished episode) -- the RCCL gather payload. */
 int prl_batch_get_returns(PrlBatch *batch, double *episode_return, void *stream);
 

@@ -89,11 +89,13 @@ SYMBOLS = {
     'prl_batch_get_state': (C.c_int, [_vp, _vp, _vp]),
     'prl_batch_get_thickness': (C.c_int, [_vp, _vp, _vp]),
     'prl_batch_get_returns': (C.c_int, [_vp, _vp, _vp]),
+    'prl_batch_export': (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'prl_batch_import': (C.c_int, [_vp, C.c_int, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'prl_ray_batch': (C.c_int, [_vp, C.c_int, _vp, _vp, _vp, _vp, _vp, _vp]),
     'prl_batch_timing_enable': (C.c_int, [_vp, C.c_int]),
     'prl_batch_timing_read': (C.c_int, [_vp, _dp, C.POINTER(C.c_int64)]),
 }
-ABI_VERSION = 3          # 3: + prl_batch_step_occupancy, prl_batch_get_last_mask (round 5)
+ABI_VERSION = 3          # 3: + prl_batch_step_occupancy, prl_batch_get_last_mask (round 5); + prl_batch_export, prl_batch_import (added symbols only)
 _lib = None
 
 

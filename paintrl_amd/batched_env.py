@@ -193,6 +193,104 @@ class BatchedPaintEnv(object):
             _lib.check(self.lib.prl_batch_observe(self._batch, self._ptr(obs), self._stream()), 'prl_batch_observe')
         return obs
 
+    # ------------------------------------------------------------------ snapshots (paintrl_amd.snapshot, prl_batch_export / import)
+    def _env_index(self, envs, what):
+        idx = np.arange(self.n_envs, dtype=np.int32) if envs is None else np.asarray(envs, dtype=np.int64).reshape(-1)
+        if idx.size and (idx.min() < 0 or idx.max() >= self.n_envs):
+            raise _lib.PaintRLError('%s: env index out of range 0..%d' % (what, self.n_envs - 1))
+        return idx.astype(np.int32)
+
+    def snapshot(self, envs=None):
+        """EnvSnapshot of envs ``envs`` (default: all, in order): device copies of their state records, coverage, last-shot
+        and (HSI) thickness rows, one stream-ordered export launch.  ``obs`` is not part of it (``restore`` recomputes it)."""
+        from .snapshot import EnvSnapshot
+        torch = _torch()
+        idx = self._env_index(envs, 'snapshot')
+        n, ms = idx.size, self.mask_stride
+        with torch.cuda.device(self.device):
+            rows = (torch.empty((n, _lib.STATE_DOUBLES), dtype=torch.float64, device=self.device),
+                    torch.empty((n, ms), dtype=torch.int64, device=self.device),
+                    torch.empty((n, ms), dtype=torch.int64, device=self.device),
+                    torch.empty((n, 64 * ms), dtype=torch.uint8, device=self.device) if self.cfg.color_mode == 1 else None,
+                    torch.empty(n, dtype=torch.int32, device=self.device))
+            env_idx = None if envs is None else torch.from_numpy(idx).to(self.device)
+            self.snapshot_into(env_idx, *rows, n=n)
+        return EnvSnapshot(self.env_part_id[idx], [p.fingerprint() for p in self.parts], [p.n_samples for p in self.parts],
+                           'HSI' if self.cfg.color_mode == 1 else 'RGB', device_rows=rows, tables=self.parts, mask_stride=ms)
+
+    def snapshot_into(self, env_idx, state, painted, last, thick, part, n=None):
+        """Raw export (``prl_batch_export``) into caller-owned device tensors: float64 (n, 16), int64 (n, mask_stride) twice,
+        uint8 (n, 64 * mask_stride) or None (HSI only), int32 (n,); ``env_idx`` int32 (n,) device tensor or None (= envs 0..n-1).
+        No checks, no allocations."""
+        n = int(part.shape[0] if n is None else n)
+        _lib.check(self.lib.prl_batch_export(self._batch, n, self._ptr(env_idx), self._ptr(state), self._ptr(painted),
+                                             self._ptr(last), self._ptr(thick), self._ptr(part), self._stream()),
+                   'prl_batch_export')
+
+    def restore_raw(self, env_idx, row_idx, state, painted, last, thick, part, n=None, n_skipped=None):
+        """Raw import (``prl_batch_import``) from device tensors in this batch's layout (what ``snapshot_into`` writes; ``part``
+        holds part ids of THIS batch): env ``env_idx[k]`` <- row ``row_idx[k]`` for k < n (None = identity; ``n`` defaults to
+        the number of rows).  Pairs out of range or across parts are skipped and added to ``n_skipped`` (int32 (1,) device
+        tensor, or None).  No checks, no allocations, no synchronisation: the hot-loop variant of ``restore``."""
+        n_rows = int(part.shape[0])
+        n = int(n_rows if n is None else n)
+        _lib.check(self.lib.prl_batch_import(self._batch, n, n_rows, self._ptr(env_idx), self._ptr(row_idx), self._ptr(state),
+                                             self._ptr(painted), self._ptr(last), self._ptr(thick), self._ptr(part),
+                                             self._ptr(n_skipped), self._stream()), 'prl_batch_import')
+
+    def restore(self, snap, envs=None, rows=None):
+        """Write snapshot rows ``rows`` into envs ``envs`` (defaults: rows 0..len-1 into envs 0..len-1, or the identity over
+        whichever is given).  Parts are matched by fingerprint and the color mode must agree (PaintRLError otherwise, nothing
+        written).  A pair whose env or row index is out of range, or whose parts differ, is skipped -- its env keeps its state
+        -- and makes this call raise PaintRLError once the others are written (one synchronisation).  Returns ``observe()``."""
+        torch = _torch()
+        if rows is None:
+            rows = np.arange(len(snap) if envs is None else np.asarray(envs).reshape(-1).size)
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        envs = np.arange(rows.size) if envs is None else np.asarray(envs, dtype=np.int64).reshape(-1)
+        if envs.size != rows.size:
+            raise ValueError('restore: %d envs but %d rows' % (envs.size, rows.size))
+        ok = (rows >= 0) & (rows < len(snap))
+        part_map = snap.part_map(self.parts, 'HSI' if self.cfg.color_mode == 1 else 'RGB', rows[ok])
+        with torch.cuda.device(self.device):
+            state, painted, last, thick, part = snap.device_rows(self, part_map)
+            i32 = lambda a: torch.from_numpy(np.clip(a, -1, 2 ** 31 - 1).astype(np.int32)).to(self.device)     # noqa: E731
+            skipped = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.restore_raw(i32(envs), i32(rows), state, painted, last, thick, part, n=rows.size, n_skipped=skipped)
+            n_bad = int(skipped.item())
+        if n_bad:
+            raise _lib.PaintRLError('restore: %d of %d (env, row) pairs skipped (index out of range or another part); '
+                                    'their envs are unchanged' % (n_bad, rows.size))
+        return self.observe()
+
+    def copy_envs(self, dst, src):
+        """env dst[k] <- env src[k] (clone: repeat a source; permute: a permutation).  Every source is read before any
+        destination is written (export, then import, on one stream).  Host index sequences are checked (range, same part);
+        int32 device tensors are taken as they are: the hot-loop form (pairs across parts are then skipped silently)."""
+        torch = _torch()
+        if isinstance(src, torch.Tensor) and isinstance(dst, torch.Tensor):
+            s, d = src, dst
+        else:
+            s_np, d_np = self._env_index(src, 'copy_envs'), self._env_index(dst, 'copy_envs')
+            if s_np.size != d_np.size:
+                raise ValueError('copy_envs: %d destinations but %d sources' % (d_np.size, s_np.size))
+            if not np.array_equal(self.env_part_id[s_np], self.env_part_id[d_np]):
+                raise _lib.PaintRLError('copy_envs: a source and its destination paint different parts')
+            s, d = torch.from_numpy(s_np).to(self.device), torch.from_numpy(d_np).to(self.device)
+        n = int(s.shape[0])
+        ms = self.mask_stride
+        buf = getattr(self, '_copy_buf', None)
+        if buf is None or buf[0].shape[0] < n:
+            with torch.cuda.device(self.device):
+                buf = (torch.empty((n, _lib.STATE_DOUBLES), dtype=torch.float64, device=self.device),
+                       torch.empty((n, ms), dtype=torch.int64, device=self.device),
+                       torch.empty((n, ms), dtype=torch.int64, device=self.device),
+                       torch.empty((n, 64 * ms), dtype=torch.uint8, device=self.device) if self.cfg.color_mode == 1 else None,
+                       torch.empty(n, dtype=torch.int32, device=self.device))
+            self._copy_buf = buf
+        self.snapshot_into(s, *buf, n=n)
+        self.restore_raw(d, None, *buf, n=n)
+
     # ------------------------------------------------------------------ read-back
     def painted_words(self):
         """int64 tensor (N, mask_stride) holding the u64 coverage words in device sample order."""
@@ -239,15 +337,8 @@ class BatchedPaintEnv(object):
         raw = torch.zeros((self.n_envs, _lib.STATE_DOUBLES), dtype=torch.float64, device=self.device)
         with torch.cuda.device(self.device):
             _lib.check(self.lib.prl_batch_get_state(self._batch, self._ptr(raw), self._stream()), 'prl_batch_get_state')
-        r = raw.cpu().numpy()
-        ints = r.view(np.int32).reshape(self.n_envs, -1)
-        return {'pose': r[:, 0:3].copy(), 'quat': r[:, 3:7].copy(), 'last_turning_angle': r[:, 7].copy(),
-                'total_reward': r[:, 8].copy(), 'total_return': r[:, 9].copy(),
-                'terminate': ints[:, 20].copy(), 'terminate_counter': ints[:, 21].copy(),
-                'last_on_part': ints[:, 22].copy(), 'step_counter': ints[:, 23].copy(),
-                'episode': ints[:, 24].view(np.uint32).astype(np.uint64), 'facet_hint': ints[:, 25].copy(),
-                'last_episode_return': r[:, 13].copy(), 'last_episode_reward': r[:, 14].copy(),
-                'last_episode_len': ints[:, 30].copy(), 'last_episode_painted': ints[:, 31].copy()}
+        from .snapshot import decode_state
+        return decode_state(raw.cpu().numpy())
 
     def state_into(self, out):
         """Copy the raw per-env state records into a caller-owned float64 (N, 16) device tensor (stream-ordered)."""

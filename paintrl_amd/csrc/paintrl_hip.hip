@@ -59,6 +59,160 @@ __global__ void gather_state_kernel(const double *state, int n, int field, doubl
     if (i < n) out[i] = state[(size_t)i * PRL_STATE_DOUBLES + field];
 }
 
+// ---------------------------------------------------------------- snapshots: prl_batch_export / prl_batch_import
+// One wave per snapshot row, rows moved in V-byte pieces per lane (V = 16 when every buffer and row start allows it, else 8):
+// a door row is 2.7 KB (13 KB with the HSI bytes), a 70 k-sample part's 18 KB, so the copies are coalesced row streams.
+struct SnapArgs {
+    const PartDev *parts;
+    const int *env_part;          // device, or nullptr (= all part 0)
+    int n, n_rows, n_envs, mask_stride, nz_stride;
+    const int *env_idx, *row_idx; // device, or nullptr (= identity)
+    // the batch's rows
+    double *b_state;
+    uint64_t *b_painted, *b_last, *b_last_nz;
+    uint8_t *b_thick;
+    // the caller's dense snapshot rows
+    double *state;
+    uint64_t *painted, *last;
+    uint8_t *thick;
+    int *part;
+    int *n_skipped;
+};
+
+typedef uint64_t u64x2 __attribute__((ext_vector_type(2)));
+template <int V> struct SnapVec { typedef uint64_t type; };
+template <> struct SnapVec<16> { typedef u64x2 type; };
+
+// pads of a word set to 0xff where `keep` (one bit per byte, V bytes) is clear
+template <int V>
+__device__ __forceinline__ typename SnapVec<V>::type pad_bytes(typename SnapVec<V>::type v, uint32_t keep) {
+    uint64_t fill[V / 8];
+#pragma unroll
+    for (int h = 0; h < V / 8; ++h) {
+        uint64_t f = 0;
+#pragma unroll
+        for (int b = 0; b < 8; ++b) f |= ((keep >> (8 * h + b)) & 1) ? 0 : 0xffull << (8 * b);
+        fill[h] = f;
+    }
+    if constexpr (V == 16) return v | u64x2{fill[0], fill[1]};
+    else return v | fill[0];
+}
+
+// bits 0..31 of x to the even bit positions of the result
+__device__ __forceinline__ uint64_t spread_even(uint64_t x) {
+    x &= 0xffffffffull;
+    x = (x | (x << 16)) & 0x0000ffff0000ffffull;
+    x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
+    x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    x = (x | (x << 1)) & 0x5555555555555555ull;
+    return x;
+}
+
+template <int V>
+__device__ __forceinline__ void copy_row(const uint8_t *src, uint8_t *dst, size_t bytes, int lane) {
+    typedef typename SnapVec<V>::type vec;
+    const vec *s = reinterpret_cast<const vec *>(src);
+    vec *d = reinterpret_cast<vec *>(dst);
+    for (size_t i = lane; i < bytes / V; i += 64) d[i] = s[i];
+}
+
+// snapshot row k <- env env_idx[k]; an env index out of range gives part[k] = -1 (the row is not written otherwise)
+template <int V>
+__global__ __launch_bounds__(256) void export_kernel(SnapArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int k = rfl(blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    if (k >= a.n) return;
+    const int env = rfl(a.env_idx ? a.env_idx[k] : k);
+    const bool in = env >= 0 && env < a.n_envs;
+    if (lane == 0) a.part[k] = in ? (a.env_part ? a.env_part[env] : 0) : -1;
+    if (!in) return;
+    if (lane < PRL_STATE_DOUBLES) a.state[(size_t)k * PRL_STATE_DOUBLES + lane] = a.b_state[(size_t)env * PRL_STATE_DOUBLES + lane];
+    const size_t mb = (size_t)a.mask_stride * 8;
+    copy_row<V>(reinterpret_cast<const uint8_t *>(a.b_painted) + env * mb, reinterpret_cast<uint8_t *>(a.painted) + k * mb, mb, lane);
+    copy_row<V>(reinterpret_cast<const uint8_t *>(a.b_last) + env * mb, reinterpret_cast<uint8_t *>(a.last) + k * mb, mb, lane);
+    if (a.thick) copy_row<V>(a.b_thick + env * 64 * mb / 8, a.thick + k * 64 * mb / 8, 64 * mb / 8, lane);
+}
+
+// env env_idx[k] <- snapshot row row_idx[k], for the pairs whose indices are in range and whose parts agree (the others are
+// counted in *n_skipped).  painted / last are ANDed with the part's valid bits, the last-shot row's index (StepArgs::last_nz) is
+// rebuilt exactly, HSI bytes of pads are forced to 255 and a facet hint outside the part's collision set becomes -1 (none).
+template <int V>
+__global__ __launch_bounds__(256) void import_kernel(SnapArgs a) {
+    typedef typename SnapVec<V>::type vec;
+    constexpr int WPV = V / 8;                       // mask words per lane access
+    const int lane = threadIdx.x & 63;
+    const int k = rfl(blockIdx.x * 4 + (int)(threadIdx.x >> 6));
+    if (k >= a.n) return;
+    const int env = rfl(a.env_idx ? a.env_idx[k] : k);
+    const int row = rfl(a.row_idx ? a.row_idx[k] : k);
+    const bool in = env >= 0 && env < a.n_envs && row >= 0 && row < a.n_rows;
+    const int pe = in ? rfl(a.env_part ? a.env_part[env] : 0) : -1;
+    if (!in || rfl(a.part[row]) != pe) {
+        if (lane == 0 && a.n_skipped) atomicAdd(a.n_skipped, 1);
+        return;
+    }
+    const PartDev &P = a.parts[pe];
+    const int n_words = P.n_words;
+    const gu64_p valid = P.word_valid;
+    if (lane < PRL_STATE_DOUBLES) {
+        double v = a.state[(size_t)row * PRL_STATE_DOUBLES + lane];
+        if (lane == 12) {                            // {u32 episode, i32 facet_hint}: the hint indexes the collision set
+            const int hint = __double2hiint(v);
+            if (hint < -1 || hint >= P.n_col_pad) v = __hiloint2double(-1, __double2loint(v));   // (the step's own rule)
+        }
+        a.b_state[(size_t)env * PRL_STATE_DOUBLES + lane] = v;
+    }
+    const int ms = a.mask_stride;
+    const vec *sp = reinterpret_cast<const vec *>(a.painted + (size_t)row * ms);
+    const vec *sl = reinterpret_cast<const vec *>(a.last + (size_t)row * ms);
+    vec *dp = reinterpret_cast<vec *>(a.b_painted + (size_t)env * ms);
+    vec *dl = reinterpret_cast<vec *>(a.b_last + (size_t)env * ms);
+    uint64_t *nz = a.b_last_nz + (size_t)env * a.nz_stride;
+    const int n_vec = ms / WPV;
+    int nz_written = 0;                              // words of the index row written so far
+    for (int c = 0; c * 64 < n_vec; ++c) {
+        const int i = c * 64 + lane;
+        const bool here = i < n_vec;
+        vec vp{}, vl{};
+        if (here) {
+            vec m;
+            if constexpr (V == 16) {
+                const int w = 2 * i;
+                m = u64x2{w < n_words ? ldg(valid, w) : 0, w + 1 < n_words ? ldg(valid, w + 1) : 0};
+            } else {
+                m = i < n_words ? ldg(valid, i) : 0;
+            }
+            vp = sp[i] & m;
+            vl = sl[i] & m;
+            dp[i] = vp;
+            dl[i] = vl;
+        }
+        // index bits: bit w & 63 of word w >> 6 for every non-zero word w of the last-shot row
+        if constexpr (V == 16) {
+            const uint64_t b0 = ballot64(vl.x != 0), b1 = ballot64(vl.y != 0);
+            const uint64_t lo = spread_even(b0) | (spread_even(b1) << 1), hi = spread_even(b0 >> 32) | (spread_even(b1 >> 32) << 1);
+            if (lane < 2 && 2 * c + lane < a.nz_stride) nz[2 * c + lane] = lane ? hi : lo;
+            nz_written = 2 * c + 2;
+        } else {
+            const uint64_t b = ballot64(vl != 0);
+            if (lane == 0 && c < a.nz_stride) nz[c] = b;
+            nz_written = c + 1;
+        }
+    }
+    if (lane >= nz_written && lane < a.nz_stride) nz[lane] = 0;
+    if (a.thick) {
+        constexpr int PER_WORD = 64 / V;                 // lane accesses per 64-sample word
+        const vec *st = reinterpret_cast<const vec *>(a.thick + (size_t)row * 64 * ms);
+        vec *dt = reinterpret_cast<vec *>(a.b_thick + (size_t)env * 64 * ms);
+        for (int i = lane; i < ms * PER_WORD; i += 64) {
+            const int w = i / PER_WORD;
+            const uint32_t keep = w < n_words ? (uint32_t)(ldg(valid, w) >> (V * (i % PER_WORD))) & (V == 16 ? 0xffffu : 0xffu) : 0u;
+            dt[i] = pad_bytes<V>(st[i], keep);
+        }
+    }
+}
+
 // ================================================================= host side
 thread_local char g_error[512] = "";
 
@@ -1259,6 +1413,86 @@ int prl_batch_get_state(PrlBatch *b, double *state, void *stream) {
     if (!b || !state) return fail(PRL_E_INVALID, "null argument");
     HIP_TRY(hipMemcpyAsync(state, b->state, (size_t)b->n_envs * PRL_STATE_DOUBLES * sizeof(double),
                            hipMemcpyDeviceToDevice, static_cast<hipStream_t>(stream)));
+    return PRL_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the common checks of prl_batch_export / prl_batch_import; picks the lane width V (16 bytes when every buffer and row start
+// is 16-byte aligned, else 8) and fills the batch's side of the arguments
+int snapshot_args(PrlBatch *b, int n, const void *state, const void *painted, const void *last, const void *thick,
+                  const void *part, const char *what, SnapArgs &a, int &vec) {
+    if (!b) return fail(PRL_E_INVALID, "%s: null batch", what);
+    if (n < 0) return fail(PRL_E_INVALID, "%s: negative row count", what);
+    if (!state || !painted || !last || !part) return fail(PRL_E_INVALID, "%s: null state, painted, last or part buffer", what);
+    if ((thick != nullptr) != (b->thick != nullptr))
+        return fail(PRL_E_INVALID, "%s: thick must be given exactly when the batch has COLOR_MODE 'HSI' (this batch: %s)", what,
+                    b->thick ? "HSI" : "RGB");
+    if (int rc = check_device(b)) return rc;
+    const uintptr_t any = (uintptr_t)state | (uintptr_t)painted | (uintptr_t)last | (uintptr_t)thick;
+    if (any & 7) return fail(PRL_E_INVALID, "%s: state, painted, last and thick must be 8-byte aligned", what);
+    vec = (any & 15) == 0 && b->mask_stride % 2 == 0 ? 16 : 8;
+    a = SnapArgs{};
+    a.parts = b->parts_dev;
+    a.env_part = b->env_part_dev;
+    a.n = n;
+    a.n_envs = b->n_envs;
+    a.mask_stride = b->mask_stride;
+    a.nz_stride = b->nz_stride;
+    a.b_state = b->state;
+    a.b_painted = b->painted;
+    a.b_last = b->last;
+    a.b_last_nz = b->last_nz;
+    a.b_thick = b->thick;
+    return PRL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int prl_batch_export(PrlBatch *b, int n, const int32_t *env_idx, double *state, uint64_t *painted, uint64_t *last,
+                     uint8_t *thick, int32_t *part, void *stream) {
+    SnapArgs a;
+    int vec = 8;
+    if (int rc = snapshot_args(b, n, state, painted, last, thick, part, "prl_batch_export", a, vec)) return rc;
+    if (n == 0) return PRL_OK;
+    a.env_idx = env_idx;
+    a.state = state;
+    a.painted = painted;
+    a.last = last;
+    a.thick = thick;
+    a.part = part;
+    const dim3 grid((unsigned)((n + 3) / 4)), block(256);
+    if (vec == 16) hipLaunchKernelGGL(export_kernel<16>, grid, block, 0, static_cast<hipStream_t>(stream), a);
+    else hipLaunchKernelGGL(export_kernel<8>, grid, block, 0, static_cast<hipStream_t>(stream), a);
+    HIP_TRY(hipGetLastError());
+    return PRL_OK;
+}
+
+int prl_batch_import(PrlBatch *b, int n, int n_rows, const int32_t *env_idx, const int32_t *row_idx, const double *state,
+                     const uint64_t *painted, const uint64_t *last, const uint8_t *thick, const int32_t *part,
+                     int32_t *n_skipped, void *stream) {
+    SnapArgs a;
+    int vec = 8;
+    if (int rc = snapshot_args(b, n, state, painted, last, thick, part, "prl_batch_import", a, vec)) return rc;
+    if (n_rows < 0) return fail(PRL_E_INVALID, "prl_batch_import: negative snapshot row count");
+    if (n == 0) return PRL_OK;
+    a.n_rows = n_rows;
+    a.env_idx = env_idx;
+    a.row_idx = row_idx;
+    a.state = const_cast<double *>(state);               // (read only: SnapArgs serves both directions)
+    a.painted = const_cast<uint64_t *>(painted);
+    a.last = const_cast<uint64_t *>(last);
+    a.thick = const_cast<uint8_t *>(thick);
+    a.part = const_cast<int32_t *>(part);
+    a.n_skipped = n_skipped;
+    const dim3 grid((unsigned)((n + 3) / 4)), block(256);
+    if (vec == 16) hipLaunchKernelGGL(import_kernel<16>, grid, block, 0, static_cast<hipStream_t>(stream), a);
+    else hipLaunchKernelGGL(import_kernel<8>, grid, block, 0, static_cast<hipStream_t>(stream), a);
+    HIP_TRY(hipGetLastError());
     return PRL_OK;
 }
 

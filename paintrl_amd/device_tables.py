@@ -8,6 +8,8 @@ Layout decisions (DESIGN.md "Data layout in HBM"):
     table keeps a principal-plane bounding box and a valid-bit mask;
   * collision triangles are SoA (v0, e1, e2 components) with a float32 box each.
 """
+import hashlib
+
 import numpy as np
 
 from . import _lib
@@ -314,6 +316,17 @@ class DeviceTables(object):
         s.n_beams = self.beams.shape[0]
         s.beams = dp(self.beams)
         return s
+
+    def fingerprint(self):
+        """SHA-256 (hex) of the canonical sample positions, their count and the paint radius: what a coverage row means.
+        Snapshots (paintrl_amd.snapshot) name their parts by it."""
+        if getattr(self, '_fingerprint', None) is None:
+            h = hashlib.sha256(b'paintrl samples v1')
+            h.update(np.int64(self.n_samples).tobytes())
+            h.update(np.float64(self.paint_radius).tobytes())
+            h.update(np.ascontiguousarray(self.tables.sample_pos, dtype=np.float64).tobytes())
+            self._fingerprint = h.hexdigest()
+        return self._fingerprint
 
     def mask_to_canonical(self, words):
         """u64[..., n_words] device-order coverage words -> bool[..., P] in canonical sample order

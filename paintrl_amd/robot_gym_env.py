@@ -218,6 +218,22 @@ class PaintGymEnv(spaces.Env):
         self.robot.angle_diff = 0.0
         return obs
 
+    def get_state(self):
+        """Everything ``step()`` continues from: the env's snapshot (paintrl_amd.snapshot.EnvSnapshot; ``save`` writes it to
+        a file) and this wrapper's own counters -- the step counter, ``robot.angle_diff`` and, with rollout=True, the replay
+        buffer.  Python's ``random`` module, which ``reset()`` draws from, is the caller's to save."""
+        return {'snapshot': self._batch.snapshot(), 'step_counter': self._step_counter,
+                'angle_diff': self.robot.angle_diff, 'replay_buffer': list(self.replay_buffer) if self._rollout else None}
+
+    def set_state(self, s):
+        """Restore what ``get_state`` returned: ``step()`` then continues exactly as the saved env would have."""
+        self._batch.restore(s['snapshot'])
+        self._step_counter = int(s['step_counter'])
+        self.robot.angle_diff = float(s['angle_diff'])
+        if self._rollout and s.get('replay_buffer') is not None:
+            self.replay_buffer = list(s['replay_buffer'])
+        self._refresh_state()
+
     def get_texture_image(self):
         """Part.get_texture_image() (bpw:737-738): the reference's texel list as a uint8 (W, H, 3) array -- texels outside
         the profiles black, the back side's (0, 255, 0), unpainted front texels (191, 191, 191), painted ones (255, 0, 0),
